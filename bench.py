@@ -22,10 +22,21 @@ torch.distributed.run itself as a child process (before anything touches the
 GPU) and exits with its status.  `--dry-run` exercises the rank launch and
 the process group on CPU (gloo) without touching a GPU.
 
-After the timed steps every object of the timed batch is checked: all k+m
-fragments (headers included) against the CPU oracle's encode, and the decoded
-(or reconstructed) output against the object (or the oracle's fragment).
-Any mismatch exits non-zero; the JSON line carries "verified": true.
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline
+figure needs: set-up, clock settle, W warmup steps, K timed steps, then the
+JSON line (`ms_per_step` = wall milliseconds of one timed step; `kernels` and
+`roofline` come from the timed steps' own events).  `--dump-outputs DIR`
+writes what the last timed step computed (see dump_outputs).  Everything else
+-- the oracle check of the timed batch, the CPU baseline, the fresh-mask,
+full-stripe, inline-CRC, host-resident, single-call, CLI and Swift call-shape
+legs -- runs only with `--full`, after the timed steps; the paragraphs below
+that describe those legs apply to `--full` runs.
+
+With `--full`, after the timed steps every object of the timed batch is
+checked: all k+m fragments (headers included) against the CPU oracle's encode,
+and the decoded (or reconstructed) output against the object (or the oracle's
+fragment).  Any mismatch exits non-zero; the JSON line carries
+"verified": true (false in a plain run: nothing was checked).
 
 Other BASELINE configs run through flags, each printing its own line:
 `--ec-type isa_l_rs_cauchy --k 12 --m 4 --obj-bytes 16777216 --global-batch 1024
@@ -71,6 +82,16 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: "
+                         "the oracle check of the timed batch, the CPU baseline and the "
+                         "fresh-mask, full-stripe, inline-CRC, host-resident, single-call, CLI "
+                         "and Swift call-shape legs (each still has its own switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed "
+                         "(parity fragments, decoded objects or rebuilt fragments) as "
+                         "DIR/<name>.npy: a fixed seeded sample of the bytes plus per-object "
+                         "byte sums over all of them, float32 / float64")
     ap.add_argument("--batch", type=int, default=256, help="objects per GPU (weak scaling)")
     ap.add_argument("--global-batch", type=int, default=0,
                     help="shard this many objects over the GPUs instead (strong scaling)")
@@ -126,7 +147,10 @@ def parse(argv=None):
                          "pyeclib_decode.py (k=4 m=2, one 1 MiB file) and the oracle")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch the ranks and the process group (gloo) without a GPU")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.config0 and not args.full:
+        ap.error("--config0 is one of the --full legs: add --full")
+    return args
 
 
 # ---------------- rank launch ----------------
@@ -905,6 +929,41 @@ def crc_encode_leg(args, codec, objs, n, k, m, bs, B, stream):
                     "headers of 4 objects checked against zlib.crc32"}
 
 
+# ---------------- --dump-outputs ----------------
+
+DUMP_SAMPLE = 4 << 20  # sampled bytes per output array: 16 MiB as float32
+
+
+def dump_outputs(dirname, outputs, rank, world):
+    """Write what the last timed step left in its output buffers, so that two
+    builds can be compared output for output (the inputs are seeded, hence the
+    same in every run with the same arguments).  `outputs` maps a name to a
+    uint8 device tensor (a view: fragments up to their used length, objects up
+    to their size).  Per output two files: `<name>_sample.npy`, the bytes at
+    DUMP_SAMPLE positions drawn once from a fixed seed (sorted, float32; the
+    whole array when it is no larger), and `<name>_bytesum.npy`, the sum of
+    every byte along the last axis (float64, exact).  Ranks beyond a single
+    one add `.rank<r>` before the extension.  Returns the file names."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    files = []
+    for name, t in outputs.items():
+        total = t.numel()
+        if total > DUMP_SAMPLE:
+            rng = np.random.Generator(np.random.PCG64(SEED + 4099))
+            flat = np.sort(rng.integers(0, total, size=DUMP_SAMPLE))
+        else:
+            flat = np.arange(total)
+        idx = tuple(torch.from_numpy(i).to(t.device) for i in np.unravel_index(flat, tuple(t.shape)))
+        sample = t[idx].to(torch.float32).cpu().numpy()
+        sums = t.sum(dim=-1, dtype=torch.int64).to(torch.float64).cpu().numpy()
+        for kind, arr in (("sample", sample), ("bytesum", sums)):
+            files.append(f"{name}_{kind}{suffix}.npy")
+            np.save(os.path.join(dirname, files[-1]), arr)
+    return files
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1006,6 +1065,12 @@ def main():
     torch.cuda.synchronize()
     shard.barrier()
     elapsed = shard.max_over_ranks(time.perf_counter() - t0)
+
+    dumped = None
+    if args.dump_outputs:
+        last = {"parity": stripes[:, k:, :fl]}
+        last.update({"decoded": out[:, :n]} if two == "decode" else {"rebuilt": rec[:, :fl]})
+        dumped = dump_outputs(args.dump_outputs, last, rank, world)
 
     enc_ms = float(np.mean([events[2 * i].elapsed_time(events[2 * i + 1])
                             for i in range(args.steps)]))
@@ -1112,10 +1177,16 @@ def main():
     }
     if args.same_device and world > 1:
         result["same_device"] = True
+    full = args.full
+    result["full"] = full
+    if dumped is not None:
+        result["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped}
+
+    # ---- everything below the headline runs with --full only ----
 
     # ---- erasures that change every step (untimed by the headline) ----
     fresh_ok = True
-    if two == "decode" and args.fresh_steps > 0:
+    if full and two == "decode" and args.fresh_steps > 0:
         fresh, fresh_ok = fresh_decode(args, codec, stripes, objs, out, stream, B, rank)
         result.update(fresh)
         steady, steady_ok = fresh_decode_steady(args, codec, stripes, objs, out, stream, B, rank,
@@ -1129,7 +1200,8 @@ def main():
     # ---- full-stripe encode: liberasurecode_encode's whole output (k data +
     # m parity fragments, headers included) in one launch per batch; the
     # verification below then checks the stripes this leg wrote ----
-    if args.full_stripe_steps > 0:
+    parity_same = True
+    if full and args.full_stripe_steps > 0:
         ev_fs = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         par_ref = p_parity.clone()  # the headline (parity-only) encode's output
         stripes[:, :k].zero_()
@@ -1157,7 +1229,8 @@ def main():
     # both back to back on this box, so the ratio is the CRC's cost; a
     # sample of headers checked against zlib's crc32 of their payloads.  An
     # auxiliary leg: recorded, never fatal to the headline ----
-    if args.crc_steps > 0 and not args.inline_crc32 and args.ec_type in ("amd_rs_vand", "liberasurecode_rs_vand"):
+    if full and args.crc_steps > 0 and not args.inline_crc32 \
+            and args.ec_type in ("amd_rs_vand", "liberasurecode_rs_vand"):
         try:
             result["encode_inline_crc32"] = crc_encode_leg(args, codec, objs, n, k, m, bs, B, stream)
         except Exception as exc:  # noqa: BLE001
@@ -1167,7 +1240,8 @@ def main():
     bad = []
     t_enc = t_two = None
     src = ""
-    if not args.no_verify:
+    verify = full and not args.no_verify
+    if verify:
         gpu_frags = stripes[:, :, :fl].cpu().numpy()
         gpu_second = (out[:, :n] if two == "decode" else rec[:, :fl]).cpu().numpy()
         t_enc, t_two, bad, src = oracle_pass(args, host, two_masks, dests, gpu_frags,
@@ -1175,11 +1249,11 @@ def main():
         del gpu_frags, gpu_second
     if not fresh_ok:
         bad.append((-1, "fresh-erasure decode"))
-    if args.full_stripe_steps > 0 and not parity_same:
+    if not parity_same:
         bad.append((-1, "headline parity differs from the full-stripe encode's"))
-    verified = bool(shard.min_over_ranks(0 if bad else 1)) and not args.no_verify
+    verified = bool(shard.min_over_ranks(0 if bad else 1)) and verify
     result["verified"] = verified
-    if not args.no_verify:
+    if verify:
         result["verified_objects"] = n_total
     if bad:
         print(f"rank {rank}: {len(bad)} mismatches vs the oracle, first: {bad[:5]}",
@@ -1188,6 +1262,7 @@ def main():
     numa_all = numa
     if rank == 0:
         result["placement"] = {"rank0": numa, "cpu_affinity": len(os.sched_getaffinity(0))}
+    if rank == 0 and full:
         from pyeclib_amd import system_liberasurecode
         result["system_liberasurecode"] = {
             "found": system_liberasurecode.probe(),
@@ -1195,12 +1270,12 @@ def main():
                     "when found, tests/test_system_liberasurecode.py pins the oracle and the GPU "
                     "path to its bytes"}
 
-    if rank == 0 and not args.no_host and w == 16:
+    if full and rank == 0 and not args.no_host and w == 16:
         result.update(host_resident(args, codec, host, stripes, masks, fs, bs))
         result.update(single_object_calls(args))
-    if rank == 0 and args.config0:
+    if full and rank == 0 and args.config0:
         result.update(config0_cli(args))
-    if rank == 0 and world == 1 and not args.no_host and w == 16:
+    if full and rank == 0 and world == 1 and not args.no_host and w == 16:
         try:
             result.update(reference_cli_bench())
         except Exception as exc:  # noqa: BLE001 -- an auxiliary leg: recorded, not fatal
@@ -1209,7 +1284,7 @@ def main():
             result.update(first_call())
         except Exception as exc:  # noqa: BLE001 -- an auxiliary leg: recorded, not fatal
             result["first_call"] = {"error": repr(exc)}
-    if rank == 0 and world == 1 and args.swift_procs and not args.no_host and w == 16:
+    if full and rank == 0 and world == 1 and args.swift_procs and not args.no_host and w == 16:
         # the Swift call shape: P processes, one ECDriver call per segment
         # (this process holds the GPU too: at most 15 workers beside it)
         sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -1228,7 +1303,7 @@ def main():
             "the first start to the last finish; us_per_call = median over processes; the "
             "callers' buffers staged through pinned memory (ECAMD_REGISTER_CALLER=1 uses them in place)")
 
-    if rank == 0 and not args.no_cpu_baseline and (world == 1 or args.cpu_baseline_all):
+    if full and rank == 0 and not args.no_cpu_baseline and (world == 1 or args.cpu_baseline_all):
         sample = min(args.cpu_sample or B, B)
         if t_enc is None or sample != B:
             t_enc, t_two, _, src = oracle_pass(args, host, two_masks, dests, sample=sample)
@@ -1289,7 +1364,7 @@ def main():
     if rank == 0:
         print(json.dumps(result), flush=True)
     shard.finish()
-    if not args.no_verify and not verified:
+    if verify and not verified:
         sys.exit(3)
 
 

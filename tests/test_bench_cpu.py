@@ -35,6 +35,42 @@ def test_gpus_flag_launches_ranks():
     assert out["n_gpus"] == 2 and out["requested_gpus"] == 2 and out["max_rank"] == 1.0
 
 
+def test_full_only_leg_needs_full():
+    with pytest.raises(SystemExit):
+        bench.parse(["--config0"])
+    args = bench.parse(["--full", "--config0"])
+    assert args.full and args.config0 and not bench.parse([]).full
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: per output a seeded sample (float32) and exact byte
+    sums along the last axis (float64); the same positions in every run; a
+    small array is written whole.  CPU tensors stand in for the device's."""
+    import torch
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    rng = np.random.Generator(np.random.PCG64(11))
+    big = rng.integers(0, 256, (6, 3, 500), dtype=np.uint8)
+    small = rng.integers(0, 256, (4, 100), dtype=np.uint8)
+    # views, as bench.py hands them over: fragments up to their used length
+    outs = {"parity": torch.from_numpy(big)[:, 1:, :477], "decoded": torch.from_numpy(small)}
+    files = bench.dump_outputs(str(tmp_path / "a"), outs, 0, 1)
+    assert sorted(files) == ["decoded_bytesum.npy", "decoded_sample.npy",
+                             "parity_bytesum.npy", "parity_sample.npy"]
+    got = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert got["parity_sample.npy"].dtype == np.float32 and got["parity_sample.npy"].shape == (1000,)
+    assert got["parity_bytesum.npy"].dtype == np.float64
+    assert np.array_equal(got["parity_bytesum.npy"], big[:, 1:, :477].sum(-1, dtype=np.int64))
+    assert np.array_equal(got["decoded_sample.npy"], small.reshape(-1))
+    assert np.array_equal(got["decoded_bytesum.npy"], small.sum(-1, dtype=np.int64))
+    # every sampled value is the byte at its (sorted, seeded) position of the view
+    flat = big[:, 1:, :477].reshape(-1)
+    pos = np.sort(np.random.Generator(np.random.PCG64(bench.SEED + 4099)).integers(0, flat.size, 1000))
+    assert np.array_equal(got["parity_sample.npy"], flat[pos])
+    again = bench.dump_outputs(str(tmp_path / "b"), outs, 1, 2)
+    assert "parity_sample.rank1.npy" in again
+    assert np.array_equal(np.load(tmp_path / "b" / "parity_sample.rank1.npy"), got["parity_sample.npy"])
+
+
 def _args(ec_type, k, m, n, second):
     return argparse.Namespace(ec_type=ec_type, k=k, m=m, obj_bytes=n, second=second)
 

@@ -25,7 +25,7 @@ def _run(script, *argv, timeout=240):
 
 
 def test_bench_two_ranks_same_device():
-    out = _run("bench.py", "--gpus", "2", "--same-device", "--batch", "8", "--steps", "2",
+    out = _run("bench.py", "--full", "--gpus", "2", "--same-device", "--batch", "8", "--steps", "2",
                "--warmup", "1", "--no-host", "--cpu-sample", "8", "--fresh-steps", "2")
     assert out["n_gpus"] == 2 and out["same_device"] is True
     assert out["verified"] is True and out["verified_objects"] == 16

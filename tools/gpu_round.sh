@@ -37,7 +37,7 @@ for s in $STEPS; do
         --timeout-method thread > $O/pytest_multirank.log 2>&1)
     tail -3 $O/pytest_multirank.log ;;
   config0)
-    (cd $R && timeout -k 10 400 python3 bench.py --no-host --no-cpu-baseline --config0 --steps 5 \
+    (cd $R && timeout -k 10 400 python3 bench.py --full --no-host --no-cpu-baseline --config0 --steps 5 \
         > $O/config0_bench.json 2> $O/config0_bench.err)
     tail -c 900 $O/config0_bench.json ;;
   sysfs)
@@ -66,7 +66,7 @@ for s in $STEPS; do
     python3 $R/tools/rocpd_timeline.py $O/prof --last 24 > $O/timeline.txt 2>&1 || true
     cat $O/timeline.txt ;;
   config3)
-    (cd $R && timeout -k 10 400 python3 bench.py --ec-type isa_l_rs_cauchy --k 12 --m 4 \
+    (cd $R && timeout -k 10 400 python3 bench.py --full --ec-type isa_l_rs_cauchy --k 12 --m 4 \
         --obj-bytes 16777216 --batch 128 --second reconstruct --steps 10 --no-host \
         > $O/config3_bench.json 2> $O/config3_bench.err)
     tail -c 700 $O/config3_bench.json ;;
@@ -74,11 +74,11 @@ for s in $STEPS; do
     (cd $R && timeout -k 10 400 python3 tools/swift_mix.py > $O/swift_mix.json 2> $O/swift_mix.err)
     head -c 400 $O/swift_mix.json ;;
   crc)
-    (cd $R && timeout -k 10 300 python3 bench.py --inline-crc32 --steps 20 --warmup 5 --no-host \
+    (cd $R && timeout -k 10 300 python3 bench.py --full --inline-crc32 --steps 20 --warmup 5 --no-host \
         --no-cpu-baseline > $O/bench_crc.json 2> $O/bench_crc.err)
     tail -c 400 $O/bench_crc.json ;;
   bench)
-    (cd $R && timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err)
+    (cd $R && timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err)
     cat $O/bench.json ;;
   prof)
     # per-dispatch kernel trace of the bench's headline steps (no extra legs,
