@@ -237,6 +237,44 @@ int ecamd_reconstruct_batch(int desc, const void *d_frags, uint64_t frag_stride,
                             const uint32_t *h_avail, const int *h_dest, void *d_out,
                             uint64_t out_stride, void *stream);
 
+/* Classify fragments resident in HBM: the batch form of
+ * force_metadata_checks / get_fragment_metadata's chksum_mismatch.
+ *
+ * Semantics.  For object o and every slot i whose bit is set in h_present[o],
+ * the fragment at d_frags + o*stripe_stride + i*frag_stride gets at most one
+ * bit, in this order:
+ *   bad_header  -- libec_version 0; for versions from 1.2.0 on, a wrong magic
+ *                  or a metadata checksum (byte 67) that is neither the zlib
+ *                  nor the legacy CRC of bytes 0..58
+ *                  (is_invalid_fragment_header); libec_version above 1.8.0; a
+ *                  wrong magic at any version; backend_id (byte 54) not the
+ *                  id this instance writes; chksum_type (byte 20) outside
+ *                  1..3; or a header that is not the batch layout's: idx != i,
+ *                  size != blocksize(obj_len), orig_data_size != obj_len;
+ *   bad_chksum  -- (header sound) chksum_mismatch (byte 53) is 1, or
+ *                  chksum_type is CHKSUM_CRC32 and chksum[0] (bytes 21..24)
+ *                  is neither crc32(0, payload, size) nor the legacy variant
+ *                  of it, whatever LIBERASURECODE_WRITE_LEGACY_CRC says.
+ * With chksum_type NONE or MD5 the payload is not read; bytes past
+ * 80 + blocksize of a slot and slots whose bit is clear are never read.
+ *
+ * h_present: n_obj bitmasks of the slots to check, NULL = all k+m.
+ * d_result: n_obj x {u32 bad_header, u32 bad_chksum}, device memory.
+ * Layout rules as ecamd_decode_batch (frag_stride % 16 == 0, frag_stride >=
+ * 80 + round_up(blocksize, 16), ecamd_layout_supported; else -EINVALIDPARAMS).
+ * Works with and without inline_crc32: the fragments' own chksum_type decides.
+ * Asynchronous on `stream`; 0 or -errno.  Never writes to d_frags. */
+int ecamd_verify_batch(int desc, const void *d_frags, uint64_t frag_stride,
+                       uint64_t stripe_stride, uint64_t obj_len, int n_obj,
+                       const uint32_t *h_present, void *d_result, void *stream);
+
+/* The header half of that classification for one 80-byte header found in
+ * slot `slot` (needs no GPU and no instance; the kernel runs the same
+ * function): 0 sound, 1 bad header, 2 sound with chksum_mismatch set; or
+ * -EINVALIDPARAMS (unknown backend_id). */
+int ecamd_classify_header(const void *hdr80, int backend_id, int slot, uint64_t blocksize,
+                          uint64_t obj_len);
+
 /* Host-resident encode: objects in host memory, parity fragments written
  * back to host memory.  Synchronous.  When both host arrays are pinned
  * (hipHostMalloc / hipHostRegister, device-mapped) the kernels read and write

@@ -185,6 +185,11 @@ _sig.update({
     "ecamd_call_phases": (ctypes.c_int, [ctypes.c_int, _P(ctypes.c_double), ctypes.c_int]),
     "ecamd_last_device_error": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64]),
     "ecamd_instance_stats": (ctypes.c_int, [ctypes.c_int, _P(ctypes.c_uint64), ctypes.c_int]),
+    "ecamd_verify_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                          ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                          _P(ctypes.c_uint32), ctypes.c_void_p, ctypes.c_void_p]),
+    "ecamd_classify_header": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_uint64, ctypes.c_uint64]),
 })
 EXPORTS = tuple(_sig)
 for _name, (_res, _args) in _sig.items():

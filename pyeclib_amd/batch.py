@@ -161,6 +161,78 @@ class BatchCodec:
             n_obj, masks, dst, _ptr(out), _stride0(out, fs), _stream(stream))
         self._check(ret, "ecamd_reconstruct_batch")
 
+    def verify(self, frags: Any, obj_len: int, present_masks: Sequence[int] | None = None,
+               out: Any = None, stream: Any = None) -> Any:
+        """Classify the fragments of (n_obj, k+m, frag_stride) stripes in HBM
+        by header and payload CRC-32 (ecamd_verify_batch; semantics in
+        include/erasurecode_amd.h).  present_masks: bit i of entry o set =
+        check slot i of object o (None: every slot of every object).
+        Returns a device int32 tensor (n_obj, 2) -- bad_header and bad_chksum
+        bitmasks per object -- filled asynchronously on `stream`; the stripes
+        are only read."""
+        import torch
+        fn = "ecamd_verify_batch"
+        n_obj = len(present_masks) if present_masks is not None else int(frags.shape[0])
+        self._check_count(fn, n_obj, frags, out)
+        self._check_rows(fn, frags)
+        if out is None:
+            out = torch.empty((n_obj, 2), dtype=torch.int32, device=frags.device)
+        elif out.dim() != 2 or int(out.shape[1]) != 2 or not out.is_contiguous() or \
+                out.element_size() != 4:
+            _native.raise_error(-_native.EINVALIDPARAMS, fn)
+        all_slots = (1 << (self.k + self.m)) - 1
+        masks = None if present_masks is None else \
+            (ctypes.c_uint32 * n_obj)(*(int(v) & all_slots for v in present_masks))
+        fs = int(frags.stride(1))
+        ret = _native.lib.ecamd_verify_batch(
+            self.handle.desc, _ptr(frags), fs, _stride0(frags, (self.k + self.m) * fs), obj_len,
+            n_obj, masks, _ptr(out), _stream(stream))
+        self._check(ret, fn)
+        return out[:n_obj]
+
+    def _verify_host(self, frags: Any, obj_len: int, present_masks: Sequence[int] | None,
+                     stream: Any) -> tuple[list[int], list[list[int]]]:
+        """verify, waited for: (present masks, [bad_header, bad_chksum] per object)."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream()
+        elif not hasattr(stream, "synchronize"):
+            stream = torch.cuda.ExternalStream(int(stream))
+        res = self.verify(frags, obj_len, present_masks, stream=stream)
+        stream.synchronize()
+        all_slots = (1 << (self.k + self.m)) - 1
+        present = [all_slots] * int(res.shape[0]) if present_masks is None else \
+            [int(v) & all_slots for v in present_masks]
+        return present, [[v & 0xFFFFFFFF for v in row] for row in res.cpu().tolist()]
+
+    def usable_masks(self, frags: Any, obj_len: int, present_masks: Sequence[int] | None = None,
+                     stream: Any = None) -> list[int]:
+        """The batch form of force_metadata_checks: per object, the present
+        slots whose fragment passed verify -- masks to hand straight to
+        decode / reconstruct as avail_masks.  Waits for `stream`."""
+        present, res = self._verify_host(frags, obj_len, present_masks, stream)
+        return [p & ~(bad_header | bad_chksum) for p, (bad_header, bad_chksum) in zip(present, res)]
+
+    def verify_report(self, frags: Any, obj_len: int, present_masks: Sequence[int] | None = None,
+                      stream: Any = None) -> list[dict]:
+        """One verify_stripe_metadata-shaped dict per object: {'status': 0},
+        or the first failure class met with the slots it names -- a bad
+        header (-207) before a bad checksum (-205), as
+        liberasurecode_verify_stripe_metadata returns.  Waits for `stream`."""
+        _, res = self._verify_host(frags, obj_len, present_masks, stream)
+        slots = range(self.k + self.m)
+        out: list[dict] = []
+        for bad_header, bad_chksum in res:
+            if bad_header:
+                out.append({"status": -_native.EBADHEADER, "reason": "Bad header",
+                            "bad_fragments": [i for i in slots if bad_header >> i & 1]})
+            elif bad_chksum:
+                out.append({"status": -_native.EBADCHKSUM, "reason": "Bad checksum",
+                            "bad_fragments": [i for i in slots if bad_chksum >> i & 1]})
+            else:
+                out.append({"status": 0})
+        return out
+
     def encode_host(self, objs: Any, obj_len: int, parity: Any) -> None:
         """Host-resident encode: objs (n_obj, obj_stride) and parity
         (n_obj, m, frag_stride) in (pinned) host memory."""

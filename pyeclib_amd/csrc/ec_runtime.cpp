@@ -29,7 +29,9 @@
 #include "crc32.hpp"
 #include "ec_crc.hpp"
 #include "ec_kernels.hpp"
+#include "ec_verify.hpp"
 #include "erasurecode_amd.h"
+#include "frag_check.hpp"
 #include "gf16.hpp"
 #include "gf8.hpp"
 #include "host_copy.hpp"
@@ -431,12 +433,16 @@ struct Instance {
   uint64_t direct_calls = 0;  // single-object calls that used the caller's pages in place
   RingSlot ring[kRing];
   int ring_pos = 0;
-  UploadCache dec_cache, rec_cache, hdr_cache;
+  UploadCache dec_cache, rec_cache, hdr_cache, ver_cache;
   hipStream_t hstream[kHostStreams] = {};  // host-resident pipeline
   DevBuf hbuf[kHostStreams];
   hipEvent_t hdone[kHostStreams] = {};
   DevBuf crc_lanes;                       // CrcLaneTables (device), the instance's CRC variant
   std::map<uint64_t, DevBuf> crc_finish;  // payload size -> CrcFinishTables (device)
+  // the other CRC variant's tables, built on the first ecamd_verify_batch
+  // (which accepts both variants, as the host checks do)
+  DevBuf crc_lanes_alt;
+  std::map<uint64_t, DevBuf> crc_finish_alt;
   // inline_crc32 chunk partials, one buffer per launch stream: a launch
   // reads and writes its own stream's buffer, so launches on different
   // streams (the staged host pipeline deals chunks over 3) never share one
@@ -594,6 +600,7 @@ struct Instance {
     dec_cache.release();
     rec_cache.release();
     hdr_cache.release();
+    ver_cache.release();
     if (ustream) (void)hipStreamSynchronize(ustream);
     for (auto& r : ring) {
       if (r.ev) {
@@ -612,6 +619,8 @@ struct Instance {
     for (auto& b : hbuf) b.release();
     crc_lanes.release();
     for (auto& kv : crc_finish) kv.second.release();
+    crc_lanes_alt.release();
+    for (auto& kv : crc_finish_alt) kv.second.release();
     for (auto& c : crc_part) c.buf.release();
     if (stream) (void)hipStreamDestroy(stream);
     if (ustream) (void)hipStreamDestroy(ustream);
@@ -1169,8 +1178,8 @@ uint32_t passes_of(const DecodeJob& J, const DescBatch& B, int o0, int o1) {
   return std::max<uint32_t>(1, static_cast<uint32_t>((rows + kRowsPerPass - 1) / kRowsPerPass));
 }
 
-const void* crc_lanes_for(Instance& I, hipError_t* err);
-const void* crc_finish_for(Instance& I, uint64_t bs, hipError_t* err);
+const void* crc_lanes_for(Instance& I, hipError_t* err, bool alt = false);
+const void* crc_finish_for(Instance& I, uint64_t bs, hipError_t* err, bool alt = false);
 size_t crc_part_bytes(int n_obj, uint64_t bs, int rows);
 
 // Launch the kernel passes for objects [o0, o1) whose descriptors (passes x
@@ -1360,32 +1369,35 @@ int run_decode(Instance& I, const DecodeJob& J, hipStream_t stream) {
 // when full, wait for the instance's own launches -- its users -- then drop
 // it).  Null on failure (*err set).
 constexpr size_t kCrcTableSizes = 64;
-const void* crc_lanes_for(Instance& I, hipError_t* err) {
+// alt: the variant the instance does not write (ecamd_verify_batch).
+const void* crc_lanes_for(Instance& I, hipError_t* err, bool alt) {
   *err = hipSuccess;
-  if (I.crc_lanes.p) return I.crc_lanes.p;
+  DevBuf& lanes = alt ? I.crc_lanes_alt : I.crc_lanes;
+  if (lanes.p) return lanes.p;
   std::unique_ptr<CrcLaneTables> host(new CrcLaneTables);
-  build_crc_lane_tables(I.legacy_crc, host.get());
-  hipError_t e = I.crc_lanes.ensure(sizeof(CrcLaneTables));
-  if (e == hipSuccess) e = hipMemcpy(I.crc_lanes.p, host.get(), sizeof(CrcLaneTables), hipMemcpyHostToDevice);
+  build_crc_lane_tables(I.legacy_crc != alt, host.get());
+  hipError_t e = lanes.ensure(sizeof(CrcLaneTables));
+  if (e == hipSuccess) e = hipMemcpy(lanes.p, host.get(), sizeof(CrcLaneTables), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    I.crc_lanes.release();
+    lanes.release();
     *err = e;
     return nullptr;
   }
-  return I.crc_lanes.p;
+  return lanes.p;
 }
 
-const void* crc_finish_for(Instance& I, uint64_t bs, hipError_t* err) {
+const void* crc_finish_for(Instance& I, uint64_t bs, hipError_t* err, bool alt) {
   *err = hipSuccess;
-  auto it = I.crc_finish.find(bs);
-  if (it == I.crc_finish.end()) {
-    if (I.crc_finish.size() >= kCrcTableSizes) {
+  std::map<uint64_t, DevBuf>& cache = alt ? I.crc_finish_alt : I.crc_finish;
+  auto it = cache.find(bs);
+  if (it == cache.end()) {
+    if (cache.size() >= kCrcTableSizes) {
       if ((*err = I.wait_streams()) != hipSuccess) return nullptr;
-      for (auto& kv : I.crc_finish) kv.second.release();
-      I.crc_finish.clear();
+      for (auto& kv : cache) kv.second.release();
+      cache.clear();
     }
     std::unique_ptr<CrcFinishTables> host(new CrcFinishTables);
-    build_crc_finish_tables(static_cast<uint32_t>(bs), I.legacy_crc, host.get());
+    build_crc_finish_tables(static_cast<uint32_t>(bs), I.legacy_crc != alt, host.get());
     DevBuf buf;
     hipError_t e = buf.ensure(sizeof(CrcFinishTables));
     if (e == hipSuccess) e = hipMemcpy(buf.p, host.get(), sizeof(CrcFinishTables), hipMemcpyHostToDevice);
@@ -1394,7 +1406,7 @@ const void* crc_finish_for(Instance& I, uint64_t bs, hipError_t* err) {
       *err = e;
       return nullptr;
     }
-    it = I.crc_finish.emplace(bs, buf).first;
+    it = cache.emplace(bs, buf).first;
   }
   return it->second.p;
 }
@@ -2083,6 +2095,64 @@ bool fragment_invalid(const uint8_t* frag, uint8_t wire_id) {
   return payload_chksum_mismatch(frag);
 }
 
+// ecamd_verify_batch (caller holds I.mu, device set): the checks above for
+// fragments resident in HBM -- frag_check.hpp's header classification and
+// the payload CRC in both variants, on the GPU (ec_verify.hip).  The masks
+// travel like decode's descriptors; the chunk partials and the per-fragment
+// state live in the launch stream's partials buffer.
+int run_verify(Instance& I, const uint8_t* frags, uint64_t frag_stride, uint64_t stripe_stride,
+               uint64_t obj_len, int n_obj, const uint32_t* h_present, uint32_t* d_result,
+               hipStream_t stream) {
+  const int n = I.k + I.m;
+  const uint64_t bs = blocksize_of(I.k, I.code.w, obj_len);
+  if (frag_stride % 16 || frag_stride < kHeaderBytes + round16(bs)) return -EINVALIDPARAMS;
+  if (stripe_stride % 16 || reinterpret_cast<uintptr_t>(frags) % 16 ||
+      reinterpret_cast<uintptr_t>(d_result) % 4)
+    return -EINVALIDPARAMS;
+  if (!layout_fits(I.k, I.m, bs, frag_stride, static_cast<uint64_t>(n_obj))) return -EINVALIDPARAMS;
+  const uint32_t all = (n >= 32 ? 0u : (1u << n)) - 1u;
+  thread_local std::vector<uint8_t> key;
+  key.resize(static_cast<size_t>(n_obj) * sizeof(uint32_t));
+  for (int o = 0; o < n_obj; ++o) put32(&key[sizeof(uint32_t) * o], h_present ? h_present[o] & all : all);
+  Upload u;
+  int rc = upload(I, I.ver_cache, key, 0, key.size(), stream,
+                  [&](uint8_t* host) {
+                    std::memcpy(host, key.data(), key.size());
+                    return 0;
+                  },
+                  &u);
+  if (rc < 0) return rc;
+  hipError_t e = I.note_stream(stream);
+  VerifyParams P{};
+  for (int v = 0; v < 2 && e == hipSuccess; ++v) {
+    const bool alt = (v == 1) != I.legacy_crc;  // v = 0: zlib's CRC, 1: the legacy one
+    if (!(P.lanes[v] = crc_lanes_for(I, &e, alt))) break;
+    P.tables[v] = crc_finish_for(I, bs, &e, alt);
+  }
+  const uint64_t state_words = verify_state_words(n_obj, n);
+  const uint64_t words = state_words + verify_part_words(n_obj, n, static_cast<uint32_t>(bs));
+  uint32_t* buf = nullptr;
+  if (e == hipSuccess) e = crc_part_for(I, stream, static_cast<size_t>(words) * sizeof(uint32_t), &buf);
+  if (e == hipSuccess) {
+    P.frags = frags;
+    P.frag_stride = frag_stride;
+    P.stripe_stride = stripe_stride;
+    P.obj_len = obj_len;
+    P.bs = static_cast<uint32_t>(bs);
+    P.n_obj = static_cast<uint32_t>(n_obj);
+    P.nfrag = static_cast<uint32_t>(n);
+    P.wire_id = I.code.wire_id;
+    P.present = reinterpret_cast<const uint32_t*>(u.dev);
+    P.state = buf;
+    P.part = buf + state_words;
+    P.result = d_result;
+    e = launch_verify(P, stream);
+  }
+  const hipError_t e2 = upload_done(I, u, stream);
+  if (e != hipSuccess) return hip_errno(e);
+  return e2 == hipSuccess ? 0 : hip_errno(e2);
+}
+
 struct Partition {
   const uint8_t* by_idx[kMaxFragments];
   int missing = 0;
@@ -2603,6 +2673,31 @@ int ecamd_reconstruct_batch(int desc, const void* d_frags, uint64_t frag_stride,
               static_cast<uint8_t*>(d_out), out_stride, n_obj, h_avail, h_dest, hdr.data()};
   J.crc = I->ct == CHKSUM_CRC32 && bs > 0;
   return run_decode(*I, J, static_cast<hipStream_t>(stream));
+}
+
+int ecamd_verify_batch(int desc, const void* d_frags, uint64_t frag_stride, uint64_t stripe_stride,
+                       uint64_t obj_len, int n_obj, const uint32_t* h_present, void* d_result,
+                       void* stream) {
+  if (n_obj < 0) return -EINVALIDPARAMS;
+  auto I = lookup(desc);
+  if (!I) return -EBACKENDNOTAVAIL;
+  if (n_obj == 0) return 0;  // nothing to classify, nothing to write
+  if (!d_frags || !d_result) return -EINVALIDPARAMS;
+  std::lock_guard<std::mutex> lk(I->mu);
+  DeviceGuard g(I->device);
+  CallScope cs(*I);
+  return run_verify(*I, static_cast<const uint8_t*>(d_frags), frag_stride, stripe_stride, obj_len,
+                    n_obj, h_present, static_cast<uint32_t*>(d_result),
+                    static_cast<hipStream_t>(stream));
+}
+
+int ecamd_classify_header(const void* hdr80, int backend_id, int slot, uint64_t blocksize,
+                          uint64_t obj_len) {
+  const Code* code = code_of(backend_id);
+  if (!hdr80 || !code || slot < 0) return -EINVALIDPARAMS;
+  uint32_t w[fragcheck::kHeaderDwords];
+  std::memcpy(w, hdr80, sizeof(w));
+  return fragcheck::classify_header(w, code->wire_id, static_cast<uint32_t>(slot), blocksize, obj_len);
 }
 
 int ecamd_encode_host_batch(int desc, const void* h_objs, uint64_t obj_stride, uint64_t obj_len,
